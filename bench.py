@@ -28,7 +28,13 @@ ranking on the 40-B vote_req_t records) and the election-win transition
 (apus_vote_win_batch: the groups whose candidate won become leaders -- on the
 first step; the cold step is timed on its own and reported under "failover").
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+       A plain run sets up, warms up, times the K steps and prints the result
+       line.  --full adds the CPU baseline (the reference's own code and the
+       restatement on the host cores, `cpu_baseline` in the line).
+       --dump-outputs DIR writes what the last timed step computed (the
+       commit call's output arrays, C3's validation, C5's election-win
+       outputs, the batch statistics) as DIR/<name>.npy, float32 / float64.
        N > 1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set)
        the world must equal N; run directly, bench.py starts
        torch.distributed.run --nproc-per-node N itself (a child process,
@@ -83,7 +89,12 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=list(WORKLOADS))
     ap.add_argument("--groups", type=int, default=0, help="override groups per GPU")
     ap.add_argument("--impl", default="wave", choices=["wave", "lane"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baseline (cpu_baseline in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; a seeded sample "
+                         "of the groups when the whole would pass 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--vote-sit", action="store_true",
                     help="A/B only: C5's ranking on packed (sid, index, term) rows derived from the 40-B vote_req "
                          "records outside the timed region (apus_batch_t.vote_sit) instead of the records")
@@ -102,7 +113,10 @@ def parse():
                     help="run the N > 1 path (RCCL process group and all-reduce) even at N = 1 (a rehearsal)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--traffic", default=None, help="PMC traffic summary (default profiles/traffic_commit_<workload>.json)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1, --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -141,6 +155,50 @@ def _cpu_model():
     except OSError:
         pass
     return ""
+
+
+DUMP_BUDGET = 48 << 20         # bytes of .npy per run (--dump-outputs): under 64 MB with every header
+
+
+def save_exact(dirpath, name, a):
+    """one integer array as DIR/<name>.npy: float32 for 8- and 16-bit
+    elements, float64 for wider ones; a 64-bit array that float64 cannot hold
+    exactly goes out as its halves, <name>_lo32 and <name>_hi32"""
+    if a.dtype.itemsize <= 2:
+        np.save(os.path.join(dirpath, name + ".npy"), a.astype(np.float32))
+        return
+    f = a.astype(np.float64)
+    if a.dtype.itemsize == 8:
+        u = np.ascontiguousarray(a).view(np.uint64)
+        if u.size and int(u.max()) >= 1 << 53:
+            np.save(os.path.join(dirpath, name + "_lo32.npy"), (u & np.uint64(0xffffffff)).astype(np.float64))
+            np.save(os.path.join(dirpath, name + "_hi32.npy"), (u >> np.uint64(32)).astype(np.float64))
+            return
+        f = u.astype(np.float64)
+    np.save(os.path.join(dirpath, name + ".npy"), f)
+
+
+def dump_outputs(dirpath, prefix, rows, named, stats, budget):
+    """--dump-outputs: the per-group output tensors `named` (name -> device
+    tensor of rows x k elements) and the batch statistics.  When the arrays
+    would pass `budget` bytes, the same seeded sample of the groups (sorted,
+    written as <prefix>sample_groups.npy) is taken from each."""
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    out_bytes = lambda t: {1: 4, 2: 4, 4: 8, 8: 16}[t.element_size()]   # noqa: E731 (8: the halves, if needed)
+    per_row = 8 + sum(t.numel() // rows * out_bytes(t) for t in named.values())
+    idx = None
+    if per_row * rows > budget:
+        keep = np.sort(np.random.default_rng(20260).choice(rows, size=max(1, budget // per_row), replace=False))
+        np.save(os.path.join(dirpath, prefix + "sample_groups.npy"), keep.astype(np.float64))
+        idx = torch.from_numpy(keep)
+    for name, t in named.items():
+        v = t.view(rows, -1)
+        if idx is not None:
+            v = v.index_select(0, idx.to(v.device))
+        a = v.cpu().numpy()
+        save_exact(dirpath, prefix + name, a[:, 0] if a.shape[1] == 1 else a)
+    save_exact(dirpath, prefix + "stats", np.asarray(stats))
 
 
 def cpu_baseline(pkg, wl, seconds):
@@ -345,11 +403,12 @@ def main():
             b += 16 + 8 * R + 8 + 8 * R + (24 * R + 16 if args.vote_sit else 40 * R) + 13 + 27
         return b * Gw
 
-    def run_wave(gid_base, Gw, warmup, steps):
+    def run_wave(gid_base, Gw, warmup, steps, dump=None):
         """one resident batch of Gw groups (ids gid_base..): generated on the
         device, then `warmup` untimed and `steps` timed steps; returns the
         timed wall seconds, the walk kernel's mean ms, its algorithmic bytes
-        per launch, the last step's statistics and the walk kernel's name"""
+        per launch, the last step's statistics and the walk kernel's name.
+        dump: (directory, file name prefix, bytes) for --dump-outputs"""
         fields = ["state", "self_idx", "remote_end", "remote_commit", "lr_step", "fail_count", "apply_offsets",
                   "prev_head", "abs_base"]
         if votes:
@@ -542,6 +601,20 @@ def main():
         tail_ms = None if (args.split or args.tail_rows) else float(np.mean([a.elapsed_time(b) for a, b in tevs]))
         win_ms = float(np.mean([a.elapsed_time(b) for a, b in wevs])) if win else None
         st = eng.stats()
+        if dump is not None:
+            # what the last timed step left in the arrays a caller passes in:
+            # the commit call's outputs, C3's validation, C5's election win
+            named = {}
+            for k, v in cout.items():
+                if isinstance(v, dict):
+                    named.update({f"{k}_{kk}": vv for kk, vv in v.items()})
+                elif torch.is_tensor(v):
+                    named[k] = v.view(torch.int64) if k == "nc_dets" else v   # (idx, term, offset) rows
+            if vout is not None:
+                named["validate"] = vout
+            if win:
+                named.update({f"win_{k}": v for k, v in wt.items() if k not in ("won", "voters", "new_commit")})
+            dump_outputs(dump[0], dump[1], Gw, named, st, dump[2])
         # algorithmic bytes of ONE launch of the dominant kernel:
         # every walked entry (64 B header + cmd.len) + 64 B group state + 1 B
         # self_idx in; 8 + 1 + 4 + 4 B out per group
@@ -573,8 +646,13 @@ def main():
     alg_bytes = tail_alg = step_bytes = val_bytes = 0
     decided = 0
     wave_log = []
-    for w0, Gw in waves:
-        r = run_wave(rank * G + w0, Gw, args.warmup, args.steps)
+    for wi, (w0, Gw) in enumerate(waves):
+        dump = None
+        if args.dump_outputs:
+            # one directory for the run: rank and wave named in the file name where there are several
+            prefix = (f"rank{rank}_" if world > 1 else "") + (f"wave{wi:02d}_" if len(waves) > 1 else "")
+            dump = (args.dump_outputs, prefix, DUMP_BUDGET // (world * len(waves)))
+        r = run_wave(rank * G + w0, Gw, args.warmup, args.steps, dump)
         st, walk_name = r["st"], r["name"]
         elapsed += r["elapsed"]
         kern_ms += r["kern_ms"]
@@ -684,7 +762,7 @@ def main():
             out["config"]["history_cmd_max_bytes"] = wl["Hmax"]
         out["roofline"]["note"] = ("kernel_ms and alg_bytes_per_launch are sums over the waves (one launch per "
                                    "wave per step); stats are the last wave's")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pkg, wl, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -8,8 +8,8 @@ SEG="--groups 4194304 --replicas 5 --entries 16 --history 2 --ring 2448"
 SQ="SQ_WAVES,SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_INSTS_VMEM_RD,SQ_WAVE_CYCLES,SQ_BUSY_CYCLES,SQ_WAIT_INST_ANY"
 case "${1:-round}" in
   round)   # the round-end evidence: suite, smoke, C2 bench + profile, C3 bench + profile
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" ;;
   nc)      # NC determinants from the walk, validation on leader determinants, fused step A/B
     $S "pytest_nc=pytest:tests/test_gpu_parity.py -k 'commit_walk_checksum_median or malformed or validate_and_nc'" \
@@ -55,20 +55,20 @@ case "${1:-round}" in
     ONLY=short_walk_checksum,short_walk KB_ARGS="$SEG" bash scripts/exp_run.sh && \
     ONLY=short_walk_checksum,short_walk KB_ARGS="$SEG" bash scripts/exp_run.sh ;;
   ev1)     # round evidence 1: the suite, smoke, C2 and C3 benches with profiles and traffic passes
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
        "pmc_c2_fetch@240=pmc:FETCH_SIZE|bench.py --no-cpu-baseline --steps 5 --warmup 1" \
        "pmc_c2_write@240=pmc:WRITE_SIZE|bench.py --no-cpu-baseline --steps 5 --warmup 1" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c3_fetch@300=pmc:FETCH_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c3_write@300=pmc:WRITE_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" ;;
   ev2)     # round evidence 2: the 64M-group batch on one GPU, the C4 shard (traffic, translation), scalar latency
     TLB="TCP_UTCL1_TRANSLATION_MISS_sum,TCP_UTCL1_TRANSLATION_HIT_sum,TCP_UTCL1_REQUEST_sum,GRBM_UTCL2_BUSY,GRBM_GUI_ACTIVE"
-    $S "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+    $S "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c41_fetch@300=pmc:FETCH_SIZE|bench.py --workload c4_1gpu --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c41_write@300=pmc:WRITE_SIZE|bench.py --workload c4_1gpu --no-cpu-baseline --steps 3 --warmup 1" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "pmc_c4_fetch@300=pmc:FETCH_SIZE|bench.py --workload c4 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c4_write@300=pmc:WRITE_SIZE|bench.py --workload c4 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c4_tlb@300=pmc:$TLB|bench.py --workload c4 --no-cpu-baseline --steps 3 --warmup 1" \
@@ -114,13 +114,13 @@ case "${1:-round}" in
     env APUS_GPU_LIB=$PWD/build_exp/libapus_lanetail.so $S "bench_c2_lane=bench:--no-cpu-baseline" \
        "bench_c41_lane=bench:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" ;;
   ev3)     # round evidence 3: the suite, smoke, every single-GPU workload with its rocprof summary
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
        "bench_c2_split=bench:--no-cpu-baseline --split" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" ;;
   c3ab)    # the C3 hop walk and the C2 wave walk: product vs the round-2 build (build_exp/libapus_r2.so), twice
     C3="--groups 262144 --replicas 5 --entries 64 --payload 64 --payload-max 4096 --ring 344064 --history 16"
@@ -163,14 +163,14 @@ case "${1:-round}" in
       ONLY=records_store,records_load KB_ARGS="--rounds 8" bash scripts/exp_run.sh || exit 1
     done ;;
   ev5)     # round evidence 5 (end of round 3): suite, smoke, every workload with its rocprof summary, C5 traffic
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c5_fetch@300=pmc:FETCH_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c5_write@300=pmc:WRITE_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" ;;
@@ -180,20 +180,20 @@ case "${1:-round}" in
        "pmc_c2_write@240=pmc:WRITE_SIZE|bench.py --no-cpu-baseline --steps 5 --warmup 1" ;;
   ev7)     # round 4 evidence, call 1: the suite, smoke, C2 and C3 (one wave and the whole batch) with
            # rocprof summaries and traffic passes
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
        "pmc_c2_fetch@240=pmc:FETCH_SIZE|bench.py --no-cpu-baseline --steps 5 --warmup 1" \
        "pmc_c2_write@240=pmc:WRITE_SIZE|bench.py --no-cpu-baseline --steps 5 --warmup 1" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c3_fetch@300=pmc:FETCH_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c3_write@300=pmc:WRITE_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" \
        "bench_c3_full@900=bench:--workload c3_full --steps 2 --warmup 1 --no-cpu-baseline" ;;
   ev8)     # round 4 evidence, call 2: C4 (shard and the 64M-group batch on one GPU) and C5, rocprof and traffic
-    $S "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c5_fetch@300=pmc:FETCH_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c5_write@300=pmc:WRITE_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
@@ -207,14 +207,14 @@ case "${1:-round}" in
        "tp_ta@120=pmc:TA_TA_BUSY_sum,TA_ADDR_STALLED_BY_TC_CYCLES_sum,GRBM_GUI_ACTIVE|$K" \
        "tp_fetch@120=pmc:FETCH_SIZE|$K" "tp_write@120=pmc:WRITE_SIZE|$K" ;;
   ev9)     # round 4 final evidence: the suite, smoke, every workload with its rocprof summary, C5 traffic
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c5_fetch@300=pmc:FETCH_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c5_write@300=pmc:WRITE_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" ;;
@@ -230,15 +230,15 @@ case "${1:-round}" in
     bash "$0" ev9 ;;
   r5ev)    # round 5 final evidence: the suite, smoke, every workload (c3_full with its CPU baseline) with its
            # rocprof summary, C2 / C5 traffic, the scalar drop-ins' latency
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --cpu-seconds 10" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --full --cpu-seconds 10" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c2_fetch@300=pmc:FETCH_SIZE|bench.py --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c2_write@300=pmc:WRITE_SIZE|bench.py --no-cpu-baseline --steps 3 --warmup 1" \
@@ -254,18 +254,18 @@ case "${1:-round}" in
        "pmc_c41_write@400=pmc:WRITE_SIZE|bench.py --workload c4_1gpu --no-cpu-baseline --steps 3 --warmup 1" ;;
   r5c3)    # round 5: the hop build's 12-KiB windows: the suite, smoke, C3 and the whole C3 batch with profiles and traffic
     $S "pytest_gpu@900=pytest" "smoke@300=smoke" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --cpu-seconds 10" \
+       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --full --cpu-seconds 10" \
        "pmc_c3_fetch@300=pmc:FETCH_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c3_write@300=pmc:WRITE_SIZE|bench.py --workload c3 --no-cpu-baseline --steps 3 --warmup 1" ;;
   r5seg)   # round 5: the segment walk's checksum builds at 3 waves per SIMD: the suite, smoke, a same-ring A/B
            # against the previous build, C5 and the 64M-group batch with profiles and traffic
     $S "pytest_gpu@900=pytest" "smoke@300=smoke" \
        "ab_seg3@400=sh:ab_seg3.sh" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
        "pmc_c5_fetch@300=pmc:FETCH_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
        "pmc_c5_write@300=pmc:WRITE_SIZE|bench.py --workload c5 --no-cpu-baseline --steps 3 --warmup 1" \
@@ -275,15 +275,15 @@ case "${1:-round}" in
     bash scripts/gpu_plan.sh r5ev && bash scripts/gpu_plan.sh r5traf ;;
   r6ev)    # round 6 evidence: the suite, smoke, every workload (c3_full with its CPU baseline) with its rocprof
            # summary, C5 with the packed request rows, and every workload's FETCH_SIZE / WRITE_SIZE passes
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
-       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --cpu-seconds 6" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
+       "bench_c3=bench:--workload c3 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c3=prof:--workload c3 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --cpu-seconds 10" \
-       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c3_full@900=bench:--workload c3_full --steps 3 --warmup 1 --full --cpu-seconds 10" \
+       "bench_c4=bench:--workload c4 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c4=prof:--workload c4 --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --cpu-seconds 8" \
+       "bench_c4_1gpu=bench:--workload c4_1gpu --steps 20 --warmup 3 --full --cpu-seconds 8" \
        "prof_c4_1gpu=prof:--workload c4_1gpu --steps 20 --warmup 3 --no-cpu-baseline" \
-       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --cpu-seconds 6" \
+       "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --full --cpu-seconds 6" \
        "prof_c5=prof:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "bench_c5_sit=bench:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline --vote-sit" \
        "pmc_c2_fetch@300=pmc:FETCH_SIZE|bench.py --no-cpu-baseline --steps 3 --warmup 1" \
@@ -305,7 +305,7 @@ case "${1:-round}" in
        "kb_app@300=kb:--rounds 5 --only append,persist" \
        "scalar=scalar:--calls 3000" ;;
   r6chk)   # round 6: the rebuilt tree on a fresh box -- the suite, smoke, C2 with its profile, C5
-    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" \
+    $S "pytest_gpu@900=pytest" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" \
        "bench_c5=bench:--workload c5 --steps 20 --warmup 3 --no-cpu-baseline" \
        "bench_c2_rccl=bench:--rccl --no-cpu-baseline --steps 20 --warmup 0" \
        "trun_c2_rccl=trun:--rccl --no-cpu-baseline --steps 20 --warmup 1" ;;
@@ -318,7 +318,7 @@ case "${1:-round}" in
   r6win)   # round 6: the C5 shard's election win, every group, against oracle/_ref
     $S "whole_win@900=pytest:tests/test_whole_batch.py -v --durations=0 -k election_win" ;;
   r6fin)   # round 6, the final tree: the whole suite (whole-batch parity included), smoke, C2 with its profile
-    $S "pytest_gpu@1100=pytest:tests --durations=25" "smoke@300=smoke" "bench_c2=bench:" "prof_c2=prof:--no-cpu-baseline" ;;
+    $S "pytest_gpu@1100=pytest:tests --durations=25" "smoke@300=smoke" "bench_c2=bench:--full" "prof_c2=prof:--no-cpu-baseline" ;;
   r6app)   # round 6: append / persist at the C2 shape
     $S "kb_app@300=kb:--rounds 5 --only append,persist" ;;
   *) echo "unknown plan $1"; exit 2 ;;
