@@ -331,8 +331,10 @@ typedef struct apus_commit_out {
                                flag, dare_ibv_rc.c:1744-1757), 0 if not,
                                0xFF if the walk hit the step guard (corrupt) */
     uint32_t *n_entries;    /* [G] entries walked and committed              */
-    uint32_t *digest;       /* [G] Adler-32 of the walked entries' immutable
-                               bytes (APUS_COMMIT_CHECKSUM; build-defined)   */
+    uint32_t *digest;       /* [G] digest of the walked entries' immutable
+                               bytes (build-defined image): Adler-32 with
+                               APUS_COMMIT_CHECKSUM, CRC-32C (RFC 3720) with
+                               APUS_COMMIT_CRC32C; one of the two per call   */
     uint64_t *median;       /* [G] DARE median-offset quorum result
                                (APUS_COMMIT_MEDIAN; dare_ibv_rc.c:1650-1723) */
     /* APUS_COMMIT_PRUNE: log_pruning's minimum in the same pass (a7,
@@ -435,6 +437,16 @@ typedef struct apus_commit_out {
  * apply_offsets, ring, sid) in the tail of a call that does not walk.      */
 #define APUS_COMMIT_PUBLISH     0x200u
 #define APUS_COMMIT_FORCE_PRUNE 0x400u
+/* a12, the blueprint's recommendation: out->digest[g] = CRC-32C (Castagnoli,
+ * reflected 0x82F63B78, init and final XOR 0xFFFFFFFF: RFC 3720 B.4, the x86
+ * / ARMv8 crc32 instructions) of the byte string APUS_COMMIT_CHECKSUM covers:
+ * the concatenated spans of the entries the walk chain visits from commit to
+ * end, bytes 27..47 of each read as zero; 0 for a group that covers nothing.
+ * Its kernels run first in the call's stream order, on the log as given; the
+ * flag implies no walk and changes no other output or statistic of the call.
+ * Refused beside APUS_COMMIT_CHECKSUM (one digest array) and beside
+ * APUS_COMMIT_FORCE_PRUNE; a NULL out->digest skips it.  Needs b->ring.     */
+#define APUS_COMMIT_CRC32C      0x800u
 
 typedef struct apus_prune_out {
     uint64_t *new_head;     /* [G] head after pruning (dare_server.c:2026-2058) */
@@ -522,6 +534,13 @@ int  apus_stats_read(apus_ctx_t *ctx, uint64_t out[APUS_STAT_COUNT],
  * Reference: update_remote_logs(), src/dare/dare_ibv_rc.c:1650-1758.       */
 int apus_commit_batch(apus_ctx_t *ctx, const apus_batch_t *b,
                       const apus_commit_out_t *out, uint32_t flags,
+                      apus_stream_t stream);
+/* a12: the CRC-32C digest alone (APUS_COMMIT_CRC32C's kernels): digest [G]
+ * (device).  Reads the batch only: no statistic is counted, no ring byte
+ * written.  Rings that are 16-B aligned take one wave per group; any other
+ * batch, APUS_BATCH_LANE_IMPL and the groups the wave form defers take one
+ * lane per group.  Same results.                                            */
+int apus_crc32c_batch(apus_ctx_t *ctx, const apus_batch_t *b, uint32_t *digest,
                       apus_stream_t stream);
 /* Measurement hook: the next apus_commit_batch call on this context launches
  * its walk kernel with `start` / `stop` (hipEvent_t, created by the caller)

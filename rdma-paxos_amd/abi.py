@@ -28,6 +28,7 @@ COMMIT_VOTE = 0x80
 COMMIT_RANK = 0x100
 COMMIT_PUBLISH = 0x200
 COMMIT_FORCE_PRUNE = 0x400
+COMMIT_CRC32C = 0x800
 FORCE_NONE, FORCE_PRUNE, FORCE_REMOVE, FORCE_REFUSED = 0, 1, 2, 3
 ABI_VERSION = 7
 BATCH_LANE_IMPL = 0x1
@@ -243,6 +244,7 @@ SIGNATURES = [
     ("apus_stats_reset", C.c_int, [vp, vp]),
     ("apus_stats_read", C.c_int, [vp, P(u64), vp]),
     ("apus_commit_batch", C.c_int, [vp, P(Batch), P(CommitOut), u32, vp]),
+    ("apus_crc32c_batch", C.c_int, [vp, P(Batch), vp, vp]),
     ("apus_commit_mark_walk", C.c_int, [vp, vp, vp]),
     ("apus_commit_mark_tail", C.c_int, [vp, vp, vp]),
     ("apus_commit_walk_info", C.c_int, [vp, P(Batch), u32, vp]),

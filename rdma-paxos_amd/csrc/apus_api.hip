@@ -205,6 +205,17 @@ int apus_commit_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_commit_ou
         apus::log_error("apus_commit_batch: ring missing or ring_stride %% 16 != 0\n");
         return APUS_ERROR;
     }
+    // one digest array: the two checksums do not combine; APUS_COMMIT_CRC32C
+    // is refused beside APUS_COMMIT_FORCE_PRUNE as APUS_COMMIT_CHECKSUM is
+    if ((flags & APUS_COMMIT_CRC32C) && (flags & (APUS_COMMIT_CHECKSUM | APUS_COMMIT_FORCE_PRUNE))) {
+        apus::log_error("apus_commit_batch: APUS_COMMIT_CRC32C does not combine with APUS_COMMIT_CHECKSUM or "
+                        "APUS_COMMIT_FORCE_PRUNE\n");
+        return APUS_ERROR;
+    }
+    if ((flags & APUS_COMMIT_CRC32C) && !b->ring) {
+        apus::log_error("apus_commit_batch: APUS_COMMIT_CRC32C needs ring\n");
+        return APUS_ERROR;
+    }
     if ((flags & APUS_COMMIT_MEDIAN) && (!b->remote_end || !b->lr_step || !b->fail_count)) {
         apus::log_error("apus_commit_batch: median needs remote_end, lr_step, fail_count\n");
         return APUS_ERROR;
@@ -252,7 +263,21 @@ int apus_commit_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_commit_ou
                         "apply_committed_entries runs between them (dare_server.c:1100-1123)\n");
         return APUS_ERROR;
     }
-    CHECK_HIP(apus::launch_commit(c, *b, *o, flags, (hipStream_t)stream));
+    // the CRC-32C of the log as given: its kernels first in the stream's order
+    if ((flags & APUS_COMMIT_CRC32C) && o->digest)
+        CHECK_HIP(apus::launch_crc32c(c, *b, o->digest, (hipStream_t)stream));
+    CHECK_HIP(apus::launch_commit(c, *b, *o, flags & ~APUS_COMMIT_CRC32C, (hipStream_t)stream));
+    return APUS_OK;
+}
+
+int apus_crc32c_batch(apus_ctx_t *c, const apus_batch_t *b, uint32_t *digest, apus_stream_t stream)
+{
+    if (!c || !batch_ok(b) || !digest || !b->ring) return APUS_ERROR;
+    if (b->n_groups >> 32) {
+        apus::log_error("apus_crc32c_batch: n_groups must be below 2^32\n");
+        return APUS_ERROR;
+    }
+    CHECK_HIP(apus::launch_crc32c(c, *b, digest, (hipStream_t)stream));
     return APUS_OK;
 }
 

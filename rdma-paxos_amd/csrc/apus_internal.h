@@ -74,6 +74,8 @@ hipError_t launch_commit(apus_ctx *ctx, const apus_batch_t &b, const apus_commit
 // the walk kernel a commit call would launch: info[0] kind (0 lane, 1 wave,
 // 2 segment), [1] hop walk, [2] block counter, [3] grid, [4] NC epilogue,
 // [5] last-determinant rows
+// CRC-32C of every group's walked image, the log as given (apus_crc.hip)
+hipError_t launch_crc32c(apus_ctx *ctx, const apus_batch_t &b, uint32_t *digest, hipStream_t s);
 hipError_t commit_walk_info(apus_ctx *ctx, const apus_batch_t &b, uint32_t flags, uint32_t *info);
 hipError_t launch_vote(apus_ctx *ctx, const apus_batch_t &b, const apus_vote_out_t &o,
                        hipStream_t s);
@@ -108,7 +110,7 @@ uint32_t grid_for(uint64_t units, uint32_t per_block, int n_cu, uint32_t per_cu)
 // the scratch of stream s, grown to at least `slots` partial-statistic slots
 // and `slow_groups` deferred-group entries (0: not needed)
 // blocks of 256 threads of kernel fn resident per CU (cached per context in
-// occ[slot]; slots 40.. belong to the non-commit kernels)
+// occ[slot]; slots 40.. belong to the non-commit kernels, 62 to crc_wave_kernel)
 int resident_blocks(apus_ctx *ctx, int slot, const void *fn);
 // A call's hold on its stream's scratch, from stream_scratch to the end of
 // the call (after its last launch): a pinned slot is never handed to another

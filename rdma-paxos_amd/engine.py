@@ -4,7 +4,7 @@ Method names follow the reference functions whose semantics the kernels
 reproduce (paths relative to the reference tree):
 
   update_remote_logs        src/dare/dare_ibv_rc.c:1650-1822  (commit walk,
-                            optional Adler-32 checksum, optional DARE median,
+                            optional Adler-32 or CRC-32C digest, optional DARE median,
                             the lazy remote-commit publish)
   force_log_pruning         src/dare/dare_server.c:2069-2122  (APUS_COMMIT_FORCE_PRUNE)
   poll_vote_count           src/dare/dare_server.c:1327-1373
@@ -88,7 +88,7 @@ class Engine:
         t = self.torch
         out = {"new_commit": self._z(G, t.int64), "committed": self._z(G, t.uint8),
                "n_entries": self._z(G, t.int32)}
-        if flags & abi.COMMIT_CHECKSUM:
+        if flags & (abi.COMMIT_CHECKSUM | abi.COMMIT_CRC32C):
             out["digest"] = self._z(G, t.int32)
         if flags & abi.COMMIT_MEDIAN:
             out["median"] = self._z(G, t.int64)
@@ -176,6 +176,17 @@ class Engine:
         o = ostruct if ostruct is not None else self.commit_struct(out)
         abi.check(self.lib.apus_commit_batch(self.ctx, C.byref(b), C.byref(o), flags, self._stream(stream)),
                   "apus_commit_batch")
+        return out
+
+    @_streamed
+    def crc32c(self, dbatch, out=None, stream=None, bstruct=None):
+        """apus_crc32c_batch: the CRC-32C (RFC 3720) of every group's walked
+        image, the log as given; returns the [G] int32 device tensor"""
+        if out is None:
+            out = self._z(dbatch.G, self.torch.int32)
+        b = bstruct if bstruct is not None else dbatch.struct()
+        abi.check(self.lib.apus_crc32c_batch(self.ctx, C.byref(b), C.c_void_p(out.data_ptr()),
+                                             self._stream(stream)), "apus_crc32c_batch")
         return out
 
     def set_commit(self, dbatch, commit):
