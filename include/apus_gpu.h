@@ -902,6 +902,149 @@ typedef struct apus_win_io {
 int apus_vote_win_batch(apus_ctx_t *ctx, const apus_batch_t *b,
                         const apus_win_io_t *io, apus_stream_t stream);
 
+/* ---- the failure detector: failure check, heartbeats, election start ----
+ * What polling() and the two timers run around the election (BASELINE config
+ * 5): heartbeat timeout -> election start -> ranking (apus_vote_rank_batch)
+ * -> tally (apus_vote_batch) -> win (apus_vote_win_batch) -> failure check /
+ * heartbeat send.  Every call is stream-ordered.  Servers i >= n_replicas
+ * have no column and are never visited (as apus_log_adjust_batch).
+ *
+ * check_failure_count (src/dare/dare_server.c:1189-1227), which polling()
+ * calls on every pass (:1013-1125).  size = get_group_size (dare_config.h:
+ * 89-97), servers in index order (:1196-1212): an OFF server is skipped; a
+ * server with fail_count >= PERMANENT_FAILURE is not counted, and is removed
+ * from a local copy of the cid (CID_SERVER_RM, bit i of `removed`) only when
+ * the local server IS_LEADER (dare_server.c:42-48) and config.cid is STABLE;
+ * every other server counts as a connection.  Then:
+ *   connections <= size / 2 (:1213-1217)                    APUS_FAIL_SHUTDOWN
+ *     the reference leaves the thread in dare_server_shutdown: neither the
+ *     configuration nor the log is changed; `removed` still reports the
+ *     disconnects the loop made;
+ *   leader and the copy differs from config.cid (:1218-1226) APUS_FAIL_REMOVED
+ *     config.cid = the copy (in place: state[g].cid, or b->cid for images),
+ *     req_id = clt_id = 0, one CONFIG entry appended by log_append_entry
+ *     (dare_log.h:466-558) at SID_GET_TERM(sid); cfg_idx = its return, 0 when
+ *     the log was full;
+ *   otherwise                                               APUS_FAIL_NONE.
+ * The host keeps dare_ib_disconnect_server for the bits of `removed` and the
+ * shutdown itself.
+ * Deviation (undefined in the reference): a CONFIG append at offsets the
+ * batched append refuses (end / tail beyond len, as APUS_FORCE_REFUSED) leaves
+ * the group unchanged (APUS_FAIL_REFUSED, APUS_STAT_CORRUPT); `removed` still
+ * reports the loop's disconnects.                                           */
+#define APUS_FAIL_NONE     0
+#define APUS_FAIL_SHUTDOWN 1
+#define APUS_FAIL_REMOVED  2
+#define APUS_FAIL_REFUSED  3
+typedef struct apus_fail_io {
+    uint64_t *req_id;       /* [G] in/out data.config.req_id                   */
+    uint16_t *clt_id;       /* [G] in/out data.config.clt_id                   */
+    uint8_t  *action;       /* [G] out APUS_FAIL_*                              */
+    uint8_t  *connections;  /* [G] out                                         */
+    uint16_t *removed;      /* [G] out: bit i = dare_ib_disconnect_server(i), or NULL */
+    uint64_t *cfg_idx;      /* [G] out: the CONFIG append's return, or NULL    */
+} apus_fail_io_t;
+
+/* needs b->ring, state (or images + cid), self_idx, sid, fail_count;
+ * b->prev_head optional (the append clears it) */
+int apus_failure_check_batch(apus_ctx_t *ctx, const apus_batch_t *b,
+                             const apus_fail_io_t *io, apus_stream_t stream);
+
+/* One tick of the heartbeat timer (hb_event, to_adjust_event) per group.
+ * io->mode picks the armed callback; mode NULL: APUS_HB_MODE_SEND for
+ * IS_LEADER groups, APUS_HB_MODE_RECEIVE for every other group (after
+ * hb_send_cb steps down the SID still says leader while the armed callback is
+ * the receive one: that caller passes the modes).
+ *
+ * APUS_HB_MODE_RECEIVE, hb_receive_cb (dare_server.c:822-922):
+ *   self >= get_group_size (:834-839): APUS_HB_NOT_MEMBER, nothing touched;
+ *   log->tail = log->len, in place (:842);
+ *   the scan over i < size skips self and OFF servers (:846-848); the leader's
+ *   slot (SID_GET_IDX(sid)) is taken from latest_hb without touching
+ *   hb[leader] when latest_hb != 0, else fetched; latest_hb is then cleared
+ *   (:849-856); every other visited slot is read and cleared by ONE atomic
+ *   fetch-and with 0 (:859); new_sid evolves as in the reference: a heartbeat
+ *   below new_sid with the L bit is an outdated leader's (bit i of `reply`,
+ *   n_outdated, :865-879), one at or above it ends the timeout and, with the L
+ *   bit, becomes new_sid (:881-887);
+ *   timeout: start_election (below)      APUS_HB_ELECTION / APUS_HB_CAS_FAILED
+ *   new_sid != sid: server_update_sid (:898-905, :2288-2297), a
+ *   compare-and-swap on the value read; the term changed (:908-912, the body
+ *   of server_to_follower is the caller's) APUS_HB_FOLLOW, else
+ *                                                          APUS_HB_SID_UPDATED
+ *   otherwise                                              APUS_HB_REARM.
+ * APUS_HB_MODE_SEND, hb_send_cb (:928-993): the visited slots (i < size, not
+ *   self, not OFF) are fetched and cleared one by one in index order; the
+ *   first with hb >= sid ends the scan (:948-959): APUS_HB_STEP_DOWN, `from`
+ *   names it, later slots are NOT touched, the SID is unchanged (the reference
+ *   swaps the SID for itself); otherwise APUS_HB_SEND (posting the heartbeats
+ *   is the host's).
+ * APUS_HB_MODE_ADJUST, to_adjust_cb (:764-817): hb[SID_GET_IDX(sid)] is
+ *   fetched and cleared (:782); nonzero: latest_hb = it, and a set
+ *   leader_failed is cleared (APUS_HB_FALSE_POSITIVE) or not
+ *   (APUS_HB_RECEIVED); zero: leader_failed = 1 (APUS_HB_MISSED).
+ * start_election (:1264-1322): sid = [term + 1 | 0 | self] by a
+ *   compare-and-swap on the value read (:1270-1279); then for i < size:
+ *   vote_ack[i] = log->len, lr_step[i] = LR_GET_WRITE, send_flag[i] = 1
+ *   (:1299-1307).
+ * The host keeps the timers and their timeouts (n_outdated: 0.1 * hb_period
+ * each, :876; a false positive: hb_period, :791), the counters of
+ * to_adjust_cb, the log-access revoke / restore, every post (heartbeats,
+ * replies of `reply`, vote requests), and server_to_follower.
+ * Deviations: a failed compare-and-swap (another writer changed the SID; the
+ * reference exits) stops the group: APUS_HB_CAS_FAILED, APUS_STAT_CORRUPT.
+ * APUS_HB_MODE_ADJUST with SID_GET_IDX(sid) >= n_replicas (the reference
+ * indexes hb[] out of bounds): nothing is read, leader_failed = 1,
+ * APUS_HB_MISSED.  The fetch-and is a relaxed system-scope atomic (a NIC
+ * writes the slots of a log-image deployment); no slot the reference leaves
+ * alone is written.  Two forms compute the same: the default stages each
+ * wave's 64 rows of hb through LDS (consecutive lanes on consecutive slots);
+ * APUS_BATCH_LANE_IMPL walks one lane per group with the reference's loop
+ * (always used for SEND groups, whose scan stops on data).                  */
+#define APUS_HB_MODE_IDLE     0   /* no timer fired: APUS_HB_IDLE              */
+#define APUS_HB_MODE_RECEIVE  1
+#define APUS_HB_MODE_SEND     2
+#define APUS_HB_MODE_ADJUST   3
+
+#define APUS_HB_IDLE            0
+#define APUS_HB_NOT_MEMBER      1
+#define APUS_HB_REARM           2
+#define APUS_HB_ELECTION        3
+#define APUS_HB_SID_UPDATED     4
+#define APUS_HB_FOLLOW          5
+#define APUS_HB_CAS_FAILED      6
+#define APUS_HB_SEND            7
+#define APUS_HB_STEP_DOWN       8
+#define APUS_HB_RECEIVED        9
+#define APUS_HB_FALSE_POSITIVE 10
+#define APUS_HB_MISSED         11
+typedef struct apus_hb_io {
+    const uint8_t *mode;          /* [G] APUS_HB_MODE_*, or NULL                 */
+    uint64_t      *latest_hb;     /* [G] in/out latest_hb_received               */
+    uint8_t       *leader_failed; /* [G] in/out                                  */
+    uint8_t       *send_flag;     /* [G][R] in/out servers[i].send_flag (election
+                                     start); NULL when no group can start one   */
+    uint8_t       *outcome;       /* [G] out APUS_HB_*                            */
+    uint16_t      *reply;         /* [G] out: bit i = dare_ib_send_hb_reply(i)   */
+    uint8_t       *n_outdated;    /* [G] out: outdated-leader heartbeats seen    */
+    uint8_t       *from;          /* [G] out: the slot that caused a step-down,
+                                     else 0xFF                                  */
+} apus_hb_io_t;
+
+/* needs b->state (or images + cid), self_idx, sid, hb, vote_ack, lr_step */
+int apus_hb_batch(apus_ctx_t *ctx, const apus_batch_t *b,
+                  const apus_hb_io_t *io, apus_stream_t stream);
+
+/* start_election alone, for groups with due[g] != 0 (the reference's other
+ * callers: dare_server.c:1171 and :2273, and :740 and :1723 likewise):
+ * outcome[g] = APUS_HB_ELECTION or
+ * APUS_HB_CAS_FAILED, APUS_HB_IDLE for the other groups.  The same device
+ * function as the timeout path.  Needs what apus_hb_batch needs less hb;
+ * send_flag as there.                                                       */
+int apus_start_election_batch(apus_ctx_t *ctx, const apus_batch_t *b,
+                              const uint8_t *due, uint8_t *send_flag,
+                              uint8_t *outcome, apus_stream_t stream);
+
 /* ---- log replication step machine ----------------------- */
 
 /* Completion status of the log-replication WR of (group g, server i), as

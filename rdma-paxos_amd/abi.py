@@ -203,6 +203,29 @@ WIN_KEYS = ("won", "voters", "new_commit", "cid_offset", "cid_idx", "req_id", "c
  WIN_CORRUPT) = range(8)
 
 
+class FailIO(C.Structure):
+    """apus_fail_io_t (check_failure_count)"""
+    _fields_ = [("req_id", vp), ("clt_id", vp), ("action", vp), ("connections", vp), ("removed", vp),
+                ("cfg_idx", vp)]
+
+
+FAIL_KEYS = ("req_id", "clt_id", "action", "connections", "removed", "cfg_idx")
+FAIL_NONE, FAIL_SHUTDOWN, FAIL_REMOVED, FAIL_REFUSED = range(4)
+
+
+class HbIO(C.Structure):
+    """apus_hb_io_t (hb_receive_cb / hb_send_cb / to_adjust_cb, start_election)"""
+    _fields_ = [("mode", vp), ("latest_hb", vp), ("leader_failed", vp), ("send_flag", vp), ("outcome", vp),
+                ("reply", vp), ("n_outdated", vp), ("from_", vp)]
+
+
+# (io dict key -> HbIO field): `from` is a Python keyword
+HB_KEYS = ("mode", "latest_hb", "leader_failed", "send_flag", "outcome", "reply", "n_outdated", "from")
+HB_MODE_IDLE, HB_MODE_RECEIVE, HB_MODE_SEND, HB_MODE_ADJUST = range(4)
+(HB_IDLE, HB_NOT_MEMBER, HB_REARM, HB_ELECTION, HB_SID_UPDATED, HB_FOLLOW, HB_CAS_FAILED, HB_SEND,
+ HB_STEP_DOWN, HB_RECEIVED, HB_FALSE_POSITIVE, HB_MISSED) = range(12)
+
+
 class LrIO(C.Structure):
     """apus_lr_io_t (handle_lr_work_completion / log_adjustment)"""
     _fields_ = [("send_flag", vp), ("send_count", vp), ("wc", vp), ("rc_connected", vp), ("nc_len", vp),
@@ -259,6 +282,9 @@ SIGNATURES = [
     ("apus_config_scan_batch", C.c_int, [vp, P(Batch), P(ConfigIO), vp]),
     ("apus_apply_batch", C.c_int, [vp, P(Batch), P(ApplyIO), vp]),
     ("apus_vote_win_batch", C.c_int, [vp, P(Batch), P(WinIO), vp]),
+    ("apus_failure_check_batch", C.c_int, [vp, P(Batch), P(FailIO), vp]),
+    ("apus_hb_batch", C.c_int, [vp, P(Batch), P(HbIO), vp]),
+    ("apus_start_election_batch", C.c_int, [vp, P(Batch), vp, vp, vp, vp]),
     ("apus_lr_completion_batch", C.c_int, [vp, P(Batch), P(LrIO), vp]),
     ("apus_log_adjust_batch", C.c_int, [vp, P(Batch), P(LrIO), vp]),
     ("apus_gen_batch", C.c_int, [vp, P(Batch), P(GenCfg), vp]),

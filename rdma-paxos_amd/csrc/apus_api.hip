@@ -383,6 +383,34 @@ int apus_vote_win_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_win_io_
     return APUS_OK;
 }
 
+int apus_failure_check_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_fail_io_t *io, apus_stream_t stream)
+{
+    if (!c || !batch_ok(b) || !io || !b->ring || !b->sid || !b->fail_count) return APUS_ERROR;
+    if (!io->req_id || !io->clt_id || !io->action || !io->connections) return APUS_ERROR;
+    CHECK_HIP(apus::launch_failure_check(c, *b, *io, (hipStream_t)stream));
+    return APUS_OK;
+}
+
+int apus_hb_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_hb_io_t *io, apus_stream_t stream)
+{
+    if (!c || !batch_ok(b) || !io || !b->sid || !b->hb || !b->vote_ack || !b->lr_step) return APUS_ERROR;
+    if (!io->latest_hb || !io->leader_failed || !io->outcome || !io->reply || !io->n_outdated || !io->from)
+        return APUS_ERROR;
+    CHECK_HIP(apus::launch_hb(c, *b, *io, nullptr, (hipStream_t)stream));
+    return APUS_OK;
+}
+
+int apus_start_election_batch(apus_ctx_t *c, const apus_batch_t *b, const uint8_t *due, uint8_t *send_flag,
+                              uint8_t *outcome, apus_stream_t stream)
+{
+    if (!c || !batch_ok(b) || !due || !outcome || !b->sid || !b->vote_ack || !b->lr_step) return APUS_ERROR;
+    apus_hb_io_t io = {};
+    io.send_flag = send_flag;
+    io.outcome = outcome;
+    CHECK_HIP(apus::launch_hb(c, *b, io, due, (hipStream_t)stream));
+    return APUS_OK;
+}
+
 int apus_lr_completion_batch(apus_ctx_t *c, const apus_batch_t *b, const apus_lr_io_t *io, apus_stream_t stream)
 {
     if (!c || !batch_ok(b) || !io || !b->lr_step || !io->wc || !io->send_flag || !io->send_count)

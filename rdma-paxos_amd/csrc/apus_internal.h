@@ -96,6 +96,9 @@ hipError_t launch_config_scan(apus_ctx *ctx, const apus_batch_t &b, const apus_c
 hipError_t launch_apply(apus_ctx *ctx, const apus_batch_t &b, const apus_apply_io_t &io, hipStream_t s);
 // the election-win transition (apus_win.hip)
 hipError_t launch_vote_win(apus_ctx *ctx, const apus_batch_t &b, const apus_win_io_t &io, hipStream_t s);
+// the failure detector (apus_hb.hip); due: apus_start_election_batch's groups, else null
+hipError_t launch_hb(apus_ctx *ctx, const apus_batch_t &b, const apus_hb_io_t &io, const uint8_t *due, hipStream_t s);
+hipError_t launch_failure_check(apus_ctx *ctx, const apus_batch_t &b, const apus_fail_io_t &io, hipStream_t s);
 // the proxy's stable-storage records (apus_records.hip)
 hipError_t launch_records_store(apus_ctx *ctx, const apus_batch_t &b, const apus_records_io_t &io, hipStream_t s);
 hipError_t launch_records_load(apus_ctx *ctx, const apus_records_load_io_t &io, hipStream_t s);

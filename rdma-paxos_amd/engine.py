@@ -14,6 +14,10 @@ reproduce (paths relative to the reference tree):
   log_entries_to_nc_buf     src/include/dare/dare_log.h:339-359
   handle_lr_work_completion src/dare/dare_ibv_rc.c:3126-3196
   log_adjustment            src/dare/dare_ibv_rc.c:1292-1451
+  check_failure_count       src/dare/dare_server.c:1189-1227
+  hb_tick                   src/dare/dare_server.c:764-993    (hb_receive_cb,
+                            hb_send_cb, to_adjust_cb)
+  start_election            src/dare/dare_server.c:1264-1322
 
 Every call goes through libapus_gpu (HIP kernels); nothing is computed here.
 """
@@ -423,6 +427,46 @@ class Engine:
         b = dbatch.struct() if bstruct is None else bstruct
         abi.check(self.lib.apus_vote_win_batch(self.ctx, C.byref(b), C.byref(w), self._stream(stream)),
                   "apus_vote_win_batch")
+        return self._io_host(io, d)
+
+    # ------------------------- failure detector: check, heartbeats, election
+    @_streamed
+    def check_failure_count(self, dbatch, io, stream=None, bstruct=None):
+        """apus_failure_check_batch (dare_server.c:1189-1227).  io: dict of
+        req_id, clt_id (in/out), action, connections, removed, cfg_idx (out)
+        as numpy (returned as numpy) or device tensors.  dbatch (cid, ring,
+        end / tail, prev_head) is updated in place."""
+        d = self._io_dev(io, abi.FAIL_KEYS)
+        f = abi.FailIO(**{k: ptr(d[k]) for k in abi.FAIL_KEYS})
+        b = dbatch.struct() if bstruct is None else bstruct
+        abi.check(self.lib.apus_failure_check_batch(self.ctx, C.byref(b), C.byref(f), self._stream(stream)),
+                  "apus_failure_check_batch")
+        return self._io_host(io, d)
+
+    @_streamed
+    def hb_tick(self, dbatch, io, stream=None, bstruct=None):
+        """apus_hb_batch: one heartbeat-timer tick per group (hb_receive_cb,
+        hb_send_cb, to_adjust_cb; dare_server.c:764-993).  io: dict of mode
+        (or None), latest_hb, leader_failed, send_flag (in/out), outcome,
+        reply, n_outdated, from (out) as numpy (returned as numpy) or device
+        tensors.  dbatch (hb, sid, tail, vote_ack, lr_step) is updated in place."""
+        d = self._io_dev(io, abi.HB_KEYS)
+        h = abi.HbIO(**{("from_" if k == "from" else k): ptr(d[k]) for k in abi.HB_KEYS})
+        b = dbatch.struct() if bstruct is None else bstruct
+        abi.check(self.lib.apus_hb_batch(self.ctx, C.byref(b), C.byref(h), self._stream(stream)), "apus_hb_batch")
+        return self._io_host(io, d)
+
+    @_streamed
+    def start_election(self, dbatch, io, stream=None, bstruct=None):
+        """apus_start_election_batch (dare_server.c:1264-1322) for the groups
+        with io["due"] != 0.  io: dict of due, send_flag (in/out), outcome
+        (out).  dbatch (sid, vote_ack, lr_step) is updated in place."""
+        keys = ("due", "send_flag", "outcome")
+        d = self._io_dev(io, keys)
+        b = dbatch.struct() if bstruct is None else bstruct
+        abi.check(self.lib.apus_start_election_batch(self.ctx, C.byref(b), ptr(d["due"]), ptr(d["send_flag"]),
+                                                     ptr(d["outcome"]), self._stream(stream)),
+                  "apus_start_election_batch")
         return self._io_host(io, d)
 
     # ------------------------------------ replication step machine (8f.2)

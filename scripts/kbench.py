@@ -342,13 +342,67 @@ def main():
         cases["records_store_lane"] = do_rstore_lane
         cases["records_load"] = lambda: lib.apus_records_load_batch(eng.ctx, C.byref(rlio), sp)
         cases["records_load_lane"] = lambda: lib.apus_records_load_batch(eng.ctx, C.byref(lio_lane), sp)
+    # ---- the failure detector in its steady state: followers whose leader's
+    # heartbeat (= the SID) has landed and whose peers are silent (REARM: R - 1
+    # slots fetched and cleared; a group whose leader is OFF in its cid times out
+    # instead), leaders whose followers are silent (SEND), and
+    # the failure check with no failed server (NONE); the heartbeat rows and the
+    # state (tail) are restored outside the timed region
+    HB_CASES = {"hb_receive", "hb_receive_lane", "hb_send", "failure_check"}
+    if want & HB_CASES:
+        gq = torch.Generator(device="cuda").manual_seed(17)
+        selfv = db.arrays["self_idx"].to(torch.int64)
+        term = torch.randint(1, 50, (G,), device="cuda", generator=gq)
+        sid_f = ((term << 9) | 256 | ((selfv + 1) % R)).contiguous()          # followers of server self + 1
+        sid_l = ((term << 9) | 256 | selfv).contiguous()                      # leaders
+        hb0 = torch.zeros(G, R, dtype=torch.int64, device="cuda")
+        hb0[torch.arange(G, device="cuda"), (selfv + 1) % R] = sid_f
+        hb_t = {"latest_hb": eng._z(G, torch.int64), "leader_failed": eng._z(G, torch.uint8),
+                "send_flag": eng._z(G, torch.uint8, R), "outcome": eng._z(G, torch.uint8),
+                "reply": eng._z(G, torch.int16), "n_outdated": eng._z(G, torch.uint8), "from_": eng._z(G, torch.uint8)}
+        hio = abi.HbIO(mode=None, **{k: v.data_ptr() for k, v in hb_t.items()})
+        f_t = {"req_id": eng._z(G, torch.int64), "clt_id": eng._z(G, torch.int16), "action": eng._z(G, torch.uint8),
+               "connections": eng._z(G, torch.uint8), "removed": eng._z(G, torch.int16),
+               "cfg_idx": eng._z(G, torch.int64)}
+        fio = abi.FailIO(**{k: v.data_ptr() for k, v in f_t.items()})
+        st_h = db.arrays["state"].clone()
+        db.arrays["fail_count"].zero_()
+        hb_b = {}
+        for name, sid, flags in (("hb_receive", sid_f, 0), ("hb_receive_lane", sid_f, abi.BATCH_LANE_IMPL),
+                                 ("hb_send", sid_l, 0), ("failure_check", sid_l, 0)):
+            hb_b[name] = db.struct()
+            hb_b[name].flags = flags
+            hb_b[name].sid = sid.data_ptr()
+
+        sid_f0, sid_l0 = sid_f.clone(), sid_l.clone()
+
+        def do_hb(name):
+            # (a timed-out group starts an election: its SID, like tail and the rows, is put back)
+            db.arrays["state"].copy_(st_h)
+            sid_f.copy_(sid_f0)
+            sid_l.copy_(sid_l0)
+            if name == "hb_send":
+                db.arrays["hb"].zero_()
+            else:
+                db.arrays["hb"].view(torch.int64).view(G, R).copy_(hb0)
+            t0.record()
+            if name == "failure_check":
+                rc = lib.apus_failure_check_batch(eng.ctx, C.byref(hb_b[name]), C.byref(fio), sp)
+            else:
+                rc = lib.apus_hb_batch(eng.ctx, C.byref(hb_b[name]), C.byref(hio), sp)
+            t1.record()
+            assert rc == 0, (name, rc)
+            return "timed"
+        for name in HB_CASES:
+            cases[name] = (lambda n: lambda: do_hb(n))(name)
     if args.only:
         cases = {k: v for k, v in cases.items() if k in want}
     times = {k: [] for k in cases}
     for r in range(args.rounds):
         for k, f in cases.items():
             if k in ("append", "append_per_group", "persist", "apply", "config_scan", "lr_completion", "log_adjust",
-                     "records_store", "records_store_lane"):  # they record their own events
+                     "records_store", "records_store_lane", "hb_receive", "hb_receive_lane", "hb_send",
+                     "failure_check"):  # they record their own events
                 f()
                 torch.cuda.synchronize()
                 times[k].append(t0.elapsed_time(t1))
@@ -420,6 +474,12 @@ def main():
            # every 24-B record read, a 16-B plan entry written
            "records_load": G * (args.entries + 16) * (24 + 16) + G * 16}
     alg["records_store_lane"], alg["records_load_lane"] = alg["records_store"], alg["records_load"]
+    # RECEIVE: state 64 + self 1 + sid 8 + latest_hb 8 + hb 8R read, the R - 1 visited slots and tail written
+    # back, 5 B of outputs (the modes are derived here: no mode byte); SEND: no latest_hb, no tail; the failure
+    # check: state 64 + self 1 + sid 8 + fail_count R read, 12 B of outputs
+    alg["hb_receive"] = alg["hb_receive_lane"] = G * (64 + 1 + 8 + 8 + 8 * R + 8 * (R - 1) + 8 + 5)
+    alg["hb_send"] = G * (64 + 1 + 8 + 8 * R + 8 * (R - 1) + 5)
+    alg["failure_check"] = G * (64 + 1 + 8 + R + 12)
     alg["append_per_group"] = alg["append"]
     alg["validate_lead"] = alg["validate"]
     for k, v in times.items():
@@ -432,6 +492,13 @@ def main():
         if k in alg:
             res[k]["GBps_alg"] = alg[k] / (med * 1e-3) / 1e9
             res[k]["Mentries_per_s"] = G * args.entries / (med * 1e-3) / 1e6
+        if k in ("hb_receive", "hb_receive_lane", "hb_send", "failure_check"):
+            # the share of the 8 TB/s peak, and what the timed call decided
+            res[k]["share_of_8TBps"] = res[k]["GBps_alg"] / 8000.0
+            cases[k]()
+            torch.cuda.synchronize()
+            codes = f_t["action"] if k == "failure_check" else hb_t["outcome"]
+            res[k]["outcomes"] = torch.bincount(codes.to(torch.int64), minlength=4).tolist()
     print(json.dumps(res, indent=1))
     eng.close()
 
